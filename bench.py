@@ -25,6 +25,13 @@ rocprofv3 PMC pass committed under profiles/ (or null).
 ``cpu_baseline``: DEAP-faithful pure-Python eaSimple (oracle/deap_port.py,
 array('d') genomes, deepcopy clone, multiprocessing.Pool map) on a bounded
 sample, rank 0 at N=1 only.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line (``roofline`` comes from events recorded inside the timed steps).
+``--full`` adds what takes work of its own: ``cpu_baseline``, the sanity
+checks and ``deme_digests`` with their check against
+profiles/deme_digests.json, and C5's stage breakdown.  ``--dump-outputs DIR``
+writes the populations the last timed step left as ``DIR/<name>.npy``.
 """
 import argparse
 import json
@@ -81,7 +88,16 @@ def parse(argv=None):
                     help="total demes, split evenly over the GPUs (C4: 8; strong scaling)")
     ap.add_argument("--mig-every", type=int, default=5)
     ap.add_argument("--mig-k", type=int, default=15)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the CPU baseline, the sanity checks and "
+                         "deme digests with their check against the committed reference, and "
+                         "(C5) the stage breakdown measured in runs of its own")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one left -- a seeded sample "
+                         "of each population's rows (genes, wvalues, valid), every fitness, the "
+                         "evaluation count -- as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample", type=int, default=65536)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--nobj", type=int, default=3,
@@ -292,6 +308,8 @@ def main(argv=None):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dry_run:
         return dry_run(args, world, rank)
+    if args.digests_out and not args.full:
+        raise SystemExit("bench.py: --digests-out needs --full (the digests are computed there)")
     if args.config == "c5":
         return bench_nsga2(args, world, rank, local)
     if args.config == "c5x":
@@ -410,23 +428,30 @@ def main(argv=None):
     if world > 1:
         kern_ms, mig_ms = max_over_ranks([kern_ms, mig_ms], device)
     nev = nevals.cpu().tolist()
-    # sanity: the populations stay valid and finite
-    for p in pops:
-        assert bool(p.valid[:n].bool().all()), "invalid fitness left after a generation"
-        # ZDT1's sqrt(f1 / g) is NaN for a gene mutated below 0 (the reference
-        # raises there); the shape run measures throughput only
-        assert problem == "zdt1" or bool(torch.isfinite(p.wvalues[:n]).all()), "non-finite fitness"
-    # correctness fingerprint of every deme after the last step (outside the
-    # timed region): the Philox streams are keyed by the deme id and the
-    # migration is exact, so a deme's digest depends only on (seed, deme id,
-    # islands, steps, migration schedule), never on how the demes are spread
-    # over ranks -- runs of the same --islands on 1, 2, 4 or 8 GPUs must print
-    # the same digests (tests/test_gpu_islands_mp.py checks the rows themselves)
-    digests = {d: deme_digest(p, n) for d, p in zip(ids, pops)}
-    if world > 1:
-        parts = [None] * world
-        dist.all_gather_object(parts, digests)
-        digests = {d: h for part in parts for d, h in part.items()}
+    if args.dump_outputs:
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, [("deme%d" % d, p) for d, p in zip(ids, pops)], n_demes,
+                     {"deme%d_nevals" % d: [nev[i][last]] for i, d in enumerate(ids)})
+    digests = None
+    if args.full:
+        # sanity: the populations stay valid and finite
+        for p in pops:
+            assert bool(p.valid[:n].bool().all()), "invalid fitness left after a generation"
+            # ZDT1's sqrt(f1 / g) is NaN for a gene mutated below 0 (the reference
+            # raises there); the shape run measures throughput only
+            assert problem == "zdt1" or bool(torch.isfinite(p.wvalues[:n]).all()), \
+                "non-finite fitness"
+        # correctness fingerprint of every deme after the last step (outside the
+        # timed region): the Philox streams are keyed by the deme id and the
+        # migration is exact, so a deme's digest depends only on (seed, deme id,
+        # islands, steps, migration schedule), never on how the demes are spread
+        # over ranks -- runs of the same --islands on 1, 2, 4 or 8 GPUs must print
+        # the same digests (tests/test_gpu_islands_mp.py checks the rows themselves)
+        digests = {d: deme_digest(p, n) for d, p in zip(ids, pops)}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, digests)
+            digests = {d: h for part in parts for d, h in part.items()}
 
     total = n * args.steps * n_demes
     value = total / elapsed
@@ -466,15 +491,18 @@ def main(argv=None):
         out["migration"] = {"ms_per_migration": round(mig_ms, 4), "every": args.mig_every,
                             "k": args.mig_k,
                             "frac_of_time": round(mig_ms * len(mig_events) / (elapsed * 1e3), 5)}
-    out["deme_digests"] = {"after_generation": args.warmup + args.steps, "seed": args.seed,
-                           "islands": n_demes,
-                           "digest": {str(d): digests[d] for d in sorted(digests)}}
-    key = digest_key(args, n, n_demes)
-    check = check_digests(key, out["deme_digests"]["digest"])
-    out["deme_digests"].update(key=key, check=check)
-    if rank == 0 and args.digests_out:
-        save_digests(args.digests_out, key, out["deme_digests"]["digest"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in ("c3", "c3r", "c2"):
+    check = None
+    if args.full:
+        out["deme_digests"] = {"after_generation": args.warmup + args.steps, "seed": args.seed,
+                               "islands": n_demes,
+                               "digest": {str(d): digests[d] for d in sorted(digests)}}
+        key = digest_key(args, n, n_demes)
+        check = check_digests(key, out["deme_digests"]["digest"])
+        out["deme_digests"].update(key=key, check=check)
+        if rank == 0 and args.digests_out:
+            save_digests(args.digests_out, key, out["deme_digests"]["digest"])
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline \
+            and args.config in ("c3", "c3r", "c2"):
         out["cpu_baseline"] = cpu_baseline(problem, args.cpu_sample)
     else:
         out["cpu_baseline"] = None
@@ -547,6 +575,47 @@ def deme_digest(pop, n):
     w = pop.wvalues[:n].contiguous().view(torch.int64)
     acc += (w * 0x632BE59BD9B4E019).sum() + pop.valid[:n].to(torch.int64).sum()
     return "%016x" % (int(acc.item()) & (2**64 - 1))
+
+
+DUMP_BYTES = 56 << 20  # of .npy files per run, all ranks together
+
+
+def dump_outputs(path, named_pops, n_pops, extra=None):
+    """``--dump-outputs DIR``: what the last timed step left, as float32 /
+    float64 ``DIR/<name>.npy``.  Per population (``n_pops`` of them in the
+    whole run share DUMP_BYTES): every wvalue and valid flag when they take at
+    most a quarter of its share, and a sample of rows -- all of them when they
+    fit, else a fixed seeded choice (``<pop>_rows``) -- with their genes (0/1
+    per gene for bits), wvalues and valid flags.  ``extra`` maps further names
+    to numbers (the evaluation counts)."""
+    import numpy as np
+    from deap_amd import _lib
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a, dtype):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a).astype(dtype))
+
+    share = DUMP_BYTES // max(1, n_pops)
+    for name, pop in named_pops:
+        n = len(pop)
+        fit_bytes = n * (pop.nobj * 8 + 4)
+        if fit_bytes <= share // 4:
+            save(name + "_wvalues_all", pop.wvalues[:n].cpu().numpy(), np.float64)
+            save(name + "_valid_all", pop.valid[:n].cpu().numpy(), np.float32)
+        else:
+            fit_bytes = 0
+        f64 = pop.gtype == _lib.DM_F64
+        row_bytes = pop.dim * (8 if f64 else 4) + pop.nobj * 8 + 4 + 8
+        r = min(n, (share - fit_bytes - 8 * 128) // row_bytes)
+        rows = np.arange(n) if r == n else np.sort(
+            np.random.default_rng(20261019).choice(n, r, replace=False))
+        g, wv, ok = pop.rows_numpy(rows)
+        save(name + "_rows", rows, np.float64)
+        save(name + "_genes", g, np.float64 if f64 else np.float32)
+        save(name + "_wvalues", wv, np.float64)
+        save(name + "_valid", ok, np.float32)
+    for name, value in (extra or {}).items():
+        save(name, value, np.float64)
 
 
 def cpu_baseline_nsga2(wv2, weights, pop, with_log=True):
@@ -821,8 +890,38 @@ def bench_nsga2(args, world=1, rank=0, local=0):
     replica_barrier(world)
     elapsed = replica_max(time.perf_counter() - t0, world, device)
     gen_ms = sum(ev[2 * s].elapsed_time(ev[2 * s + 1]) for s in range(args.steps)) / args.steps
-    # stage breakdown outside the timed region: selNSGA2 alone on 2N rows
-    # (current parents + one varOr batch of offspring)
+    out = {"metric": "individual-generations/sec @pop=2^17 DTLZ2 NSGA-II (C5)",
+           "value": round(n * args.steps * world / elapsed, 1),
+           "unit": "individual-generations/sec",
+           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "warmup_topup": {"secs": args.warmup_secs, "generations": extra_warm},
+           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "C5 NSGA-II DTLZ2 M=%d D=12 eaMuPlusLambda(mu=lambda=N) + "
+                                  "selNSGA2(2N->N)" % m, "pop": n, "genes": dim, "objectives": m,
+                      "operators": "varOr cxBlend(0.5) mutGaussian(0,0.1,1/D) cxpb=0.6 mutpb=0.3",
+                      "parallelism": "replicas%d" % world},
+           "gen_ms_events": round(gen_ms, 4),
+           "cpu_baseline": None}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("replica%d" % rank, step.combined)], world)
+    if args.full:
+        out.update(nsga2_stages(args, step, pop, tb, stream, n, m, rank, world))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    replica_finish(world)
+
+
+def nsga2_stages(args, step, pop, tb, stream, n, m, rank, world):
+    """C5 with ``--full``: the stage breakdown, in runs of its own after the
+    timed steps -- selNSGA2 alone on 2N rows (current parents + one varOr batch
+    of offspring), its count pass and front peel timed by the library's HIP
+    events -- and the CPU baseline.  Returns the result line's ``roofline``,
+    ``peel``, ``count_pass``, ``selection`` and ``cpu_baseline``."""
+    import ctypes
+    import numpy as np
+    import torch
+    from deap_amd import _lib, algorithms, tools
     comb = step.combined
     sel_ms = []
     two = pop.like(2 * n, capacity=2 * n)
@@ -911,19 +1010,7 @@ def bench_nsga2(args, world=1, rank=0, local=0):
                       "peak_basis": "32-bit VALU lane ops: 256 CU x 4 SIMD x 32 x 2.4 GHz"}
     count_pass.update({"compares_per_launch": cmp_per_sel, "compare_rate_G": round(cmp_rate, 1),
                        "unique_fits": uniq, "fronts": len(fronts)})
-    out = {"metric": "individual-generations/sec @pop=2^17 DTLZ2 NSGA-II (C5)",
-           "value": round(n * args.steps * world / elapsed, 1),
-           "unit": "individual-generations/sec",
-           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "warmup_topup": {"secs": args.warmup_secs, "generations": extra_warm},
-           "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "C5 NSGA-II DTLZ2 M=%d D=12 eaMuPlusLambda(mu=lambda=N) + "
-                                  "selNSGA2(2N->N)" % m, "pop": n, "genes": dim, "objectives": m,
-                      "operators": "varOr cxBlend(0.5) mutGaussian(0,0.1,1/D) cxpb=0.6 mutpb=0.3",
-                      "parallelism": "replicas%d" % world},
-           "gen_ms_events": round(gen_ms, 4),
-           "roofline": peel["roofline"],
+    out = {"roofline": peel["roofline"],
            "peel": peel["fronts"],
            "count_pass": count_pass,
            "selection": {"ms": round(sel_ms, 4),
@@ -932,9 +1019,7 @@ def bench_nsga2(args, world=1, rank=0, local=0):
            "cpu_baseline": None}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_nsga2(wv.cpu().numpy(), (-1.0,) * m, n)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    replica_finish(world)
+    return out
 
 
 def bench_nsga2_example(args, world=1, rank=0, local=0):
@@ -1035,7 +1120,9 @@ def bench_nsga2_example(args, world=1, rank=0, local=0):
                         "kernel": "bounded_vary_kernel (varBounded)",
                         "kernel_ms": round(v_ms, 5)},
            "cpu_baseline": None}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("replica%d" % rank, pop)], world)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the loop's CPU cost is its selNSGA2 (selTournamentDCD and the bounded
         # operators of 2^17 individuals take seconds): the C5 baseline applies
         out["cpu_baseline"] = cpu_baseline_nsga2(two.wvalues[:2 * n].cpu().numpy(), (-1.0,) * m,

@@ -15,7 +15,26 @@ def pytest_configure(config):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """A fixture archive.  One that make_golden.py wrote in pieces (NAME.npz,
+    NAME.1.npz, ...: no committed file above 1 MiB) comes back whole, as a
+    dict: the members of every piece, and an array stored as blocks of rows
+    (``key@0``, ``key@1``, ...) joined again."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    paths = [stem + ".npz"]
+    while os.path.exists("%s.%d.npz" % (stem, len(paths))):
+        paths.append("%s.%d.npz" % (stem, len(paths)))
+    if len(paths) == 1:
+        return np.load(paths[0], allow_pickle=False)
+    d = {}
+    for p in paths:
+        with np.load(p, allow_pickle=False) as z:
+            d.update((k, z[k]) for k in z.files)
+    for first in sorted(k for k in d if k.endswith("@0")):
+        key, blocks = first[:-2], []
+        while "%s@%d" % (key, len(blocks)) in d:
+            blocks.append(d.pop("%s@%d" % (key, len(blocks))))
+        d[key] = np.concatenate(blocks)
+    return d
 
 
 @pytest.fixture(scope="session")

@@ -19,6 +19,7 @@ Usage:  python tests/golden/make_golden.py            # writes tests/golden/*.np
 """
 import array
 import importlib
+import io
 import os
 import random
 import shutil
@@ -957,6 +958,38 @@ def gen_port_nsga2(D):
         json.dump(cal, f, indent=1)
 
 
+def _packed(a):
+    b = io.BytesIO()
+    np.savez_compressed(b, a=a)
+    return b.tell()
+
+
+def save_pieces(stem, arrays, limit=900 << 10):
+    """np.savez_compressed in pieces of at most `limit` bytes (stem.npz,
+    stem.1.npz, ...), so that no fixture file exceeds 1 MiB; an array too
+    large for one piece is stored as blocks of rows ``key@0``, ``key@1``, ...
+    (tests/conftest.py golden() joins the pieces and the blocks again)."""
+    items = []
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        size = _packed(a)
+        if size <= limit:
+            items.append((k, a, size))
+            continue
+        blocks = np.array_split(a, -(-size * 5 // (limit * 4)))
+        items += [("%s@%d" % (k, i), b, _packed(b)) for i, b in enumerate(blocks)]
+    pieces, cur, used = [], {}, 0
+    for k, a, size in items:
+        if cur and used + size > limit:
+            pieces.append(cur)
+            cur, used = {}, 0
+        cur[k] = a
+        used += size
+    pieces.append(cur)
+    for i, piece in enumerate(pieces):
+        np.savez_compressed("%s%s.npz" % (stem, ".%d" % i if i else ""), **piece)
+
+
 def main():
     D = load_reference()
     if sys.argv[1:] == ["log"]:
@@ -972,7 +1005,7 @@ def main():
                             **gen_selrandom(D, np.random.default_rng(5)))
         np.savez_compressed(os.path.join(HERE, "support.npz"),
                             **gen_support(D, np.random.default_rng(17)))
-        np.savez_compressed(os.path.join(HERE, "port.npz"), **gen_port(D))
+        save_pieces(os.path.join(HERE, "port"), gen_port(D))
         return
     if sys.argv[1:] == ["port_nsga2"]:
         gen_port_nsga2(D)
@@ -986,7 +1019,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "eval.npz"), **gen_eval(D, rng))
     np.savez_compressed(os.path.join(HERE, "varand.npz"), **gen_varand(D, rng))
     np.savez_compressed(os.path.join(HERE, "selection.npz"), **gen_selection(D, rng))
-    np.savez_compressed(os.path.join(HERE, "generation.npz"), **gen_ea_generation(D, rng))
+    save_pieces(os.path.join(HERE, "generation"), gen_ea_generation(D, rng))
     np.savez_compressed(os.path.join(HERE, "varor.npz"), **gen_varor(D, rng))
     np.savez_compressed(os.path.join(HERE, "nsga2.npz"), **gen_nsga2(D, rng))
     np.savez_compressed(os.path.join(HERE, "migration.npz"), **gen_migration(D, rng))

@@ -33,7 +33,7 @@ def _bench(args):
 @pytest.mark.parametrize("cfg", ["c3", "c2"])
 def test_two_ranks_on_one_gpu_match_one_rank(gpu, cfg):
     common = ["--config", cfg, "--islands", "4", "--pop", "16384", "--steps", "10",
-              "--warmup", "2", "--warmup-secs", "0.2", "--no-cpu-baseline"]
+              "--warmup", "2", "--warmup-secs", "0.2", "--full", "--no-cpu-baseline"]
     one = _bench(["--gpus", "1"] + common)
     two = _bench(["--gpus", "2", "--backend", "gloo"] + common)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2

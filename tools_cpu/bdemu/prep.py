@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Prepare library sources for the host emulation build (tools_cpu/bdemu).
 
-Extracts deap_amd/csrc/* and include/deapmi.h from a git revision (default:
-cf1cf3a^, the last tree with the m = 4 bitset kernels) or from the working
-tree ("worktree"), and rewrites the few constructs a host C++ compiler cannot
+Takes deap_amd/csrc/* and include/deapmi.h from the working tree
+("worktree"), from the snapshot of cf1cf3a^ kept in pre_deletion/ (the last
+tree with the m = 4 bitset kernels, the default; a checkout without history
+builds it too) or from any other git revision, and rewrites the few constructs a host C++ compiler cannot
 take:
 
   kernel<<<grid, block[, shm[, stream]]>>>(args);
@@ -14,8 +15,8 @@ take:
       -> out = t + a + carry-in bit `lane` of m;
   extern __shared__ ... T name[];                        -> T* name = (T*)emu::dyn_lds();
 
-The rewritten tree is build output (tools_cpu/bdemu/build/, git-ignored); no
-source is copied into the repository.  Usage: prep.py REV OUTDIR
+The rewritten tree is build output (tools_cpu/bdemu/build/, git-ignored).
+Usage: prep.py REV OUTDIR
 """
 import os
 import re
@@ -23,6 +24,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+SNAPSHOTS = {"cf1cf3a^": os.path.join(os.path.dirname(os.path.abspath(__file__)), "pre_deletion")}
 FILES = ["common.hpp", "sort.hpp", "dominance.hpp", "bitdom.hpp", "transpose.hpp",
          "dominance.hip", "bitdom.hip", "nsga2.hip"]
 
@@ -31,6 +33,12 @@ def read(rev, path):
     if rev == "worktree":
         with open(os.path.join(REPO, path)) as f:
             return f.read()
+    if rev in SNAPSHOTS:
+        try:
+            with open(os.path.join(SNAPSHOTS[rev], path)) as f:
+                return f.read()
+        except OSError:  # a file this revision does not have
+            raise subprocess.CalledProcessError(1, ["snapshot", rev, path])
     return subprocess.run(["git", "-C", REPO, "show", "%s:%s" % (rev, path)], check=True,
                           capture_output=True, text=True).stdout
 
