@@ -121,6 +121,8 @@ SIGNATURES = {
     "dm_pack_bytes": (_i64, [_PP(DevicePop), _i64]),
     "dm_mig_place": (ctypes.c_int, [_p, _PP(DevicePop), _p, _p, _i64, _p]),
     "dm_fitness_stats": (ctypes.c_int, [_p, _PP(DevicePop), _PP(_f64), _p]),
+    "dm_pareto_update": (ctypes.c_int, [_p, _PP(DevicePop), _PP(DevicePop), _PP(DevicePop), _i64,
+                                        _PP(_i64), _p]),
     "dm_sel_sample": (ctypes.c_int, [_p, _i64, _i64, Rng, _p]),
     "dm_mig_plan": (ctypes.c_int, [_i32, _PP(_i32), _PP(_i32), _i32, _i32, _p, _i32,
                                    _PP(_i32)]),

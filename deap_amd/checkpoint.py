@@ -105,7 +105,7 @@ def load(path, device=None, individual_class=None, capacity=None):
     import torch
     from .device import DevicePopulation
     from .ops import RandomStream
-    from .tools.support import HallOfFame, Logbook
+    from .tools.support import HallOfFame, Logbook, ParetoFront
     with np.load(path, allow_pickle=False) as z:
         h = json.loads(bytes(z["header"]).decode())
         if h.get("format") != FORMAT:
@@ -134,7 +134,9 @@ def load(path, device=None, individual_class=None, capacity=None):
     if h.get("logbook") is not None:
         out["logbook"] = _logbook_from_json(h["logbook"])
     if h.get("halloffame") is not None:
-        hof = HallOfFame(h["halloffame"]["maxsize"])
+        # a hall without a size bound is the Pareto archive
+        maxsize = h["halloffame"]["maxsize"]
+        hof = ParetoFront() if maxsize is None else HallOfFame(maxsize)
         items = h["halloffame"]["items"]
         if items:
             genes = np.array([g for g, _ in items])
@@ -170,7 +172,8 @@ def _as_class(ind, individual_class):
 
 
 def to_reference_types(halloffame, logbook, tools_module, individual_class=None):
-    """Rebuild a hall of fame and a logbook as ``tools_module.HallOfFame`` /
+    """Rebuild a hall of fame and a logbook as ``tools_module.HallOfFame``
+    (``tools_module.ParetoFront`` for a hall without a size bound) /
     ``tools_module.Logbook`` objects (DEAP's classes when exporting for DEAP).
     With ``individual_class`` (a DEAP creator class) the hall's entries are
     rebuilt as that class too, so unpickling needs DEAP only; without it they
@@ -181,7 +184,10 @@ def to_reference_types(halloffame, logbook, tools_module, individual_class=None)
     and the stream position."""
     hof = lb = None
     if halloffame is not None:
-        hof = tools_module.HallOfFame(halloffame.maxsize, halloffame.similar)
+        if halloffame.maxsize is None:
+            hof = tools_module.ParetoFront(halloffame.similar)
+        else:
+            hof = tools_module.HallOfFame(halloffame.maxsize, halloffame.similar)
         for ind in reversed(list(halloffame)):
             hof.insert(ind if individual_class is None else _as_class(ind, individual_class))
     if logbook is not None:

@@ -67,11 +67,11 @@ struct dm_knobs {
 };
 
 struct dm_ctx {
-    static constexpr int kSlots = 5;
+    static constexpr int kSlots = 6;
     int device = 0;
     hipStream_t stream = nullptr;
-    void* scratch[kSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[kSlots] = {0, 0, 0, 0, 0};
+    void* scratch[kSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[kSlots] = {0, 0, 0, 0, 0, 0};
     void* pinned = nullptr;  // small host staging area for host-synchronising calls
     size_t pinned_bytes = 0;
     int num_cus = 256;
@@ -161,7 +161,8 @@ namespace dm {
 // Grow-only scratch arenas; returns nullptr on failure (error set).  Growing
 // a slot discards its contents.  Slot 0 = general temporaries, 1 = NSGA-II
 // dominance matrix, 2 = NSGA-II order buffers, 3 = migration placement,
-// 4 = migration emigrant / immigrant / receive blocks.
+// 4 = migration emigrant / immigrant / receive blocks, 5 = ParetoFront update
+// (its buffers outlive the sortNondominated call inside it).
 void* scratch_slot(dm_ctx* ctx, int slot, size_t bytes);
 inline void* scratch(dm_ctx* ctx, size_t bytes) { return scratch_slot(ctx, 0, bytes); }
 void* pinned(dm_ctx* ctx, size_t bytes);

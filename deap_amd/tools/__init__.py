@@ -5,7 +5,7 @@ Crossover: ``cxTwoPoint``, ``cxBlend``, ``cxSimulatedBinaryBounded``; mutation:
 ``selWorst``, ``selNSGA2``, ``selTournamentDCD``, ``sortNondominated``
 (``emo.assignCrowdingDist``);
 migration: ``migRing``; bookkeeping: ``Statistics``, ``MultiStatistics``,
-``Logbook``, ``HallOfFame``; initialisation: ``initPopulation``.
+``Logbook``, ``HallOfFame``, ``ParetoFront``; initialisation: ``initPopulation``.
 """
 from .crossover import cxBlend, cxSimulatedBinaryBounded, cxTwoPoint
 from .emo import selNSGA2, selTournamentDCD, sortLogNondominated, sortNondominated
@@ -14,9 +14,9 @@ from .init import initPopulation
 from .migration import migRing
 from .mutation import mutFlipBit, mutGaussian, mutPolynomialBounded
 from .selection import selBest, selRandom, selTournament, selWorst
-from .support import HallOfFame, Logbook, MultiStatistics, Statistics
+from .support import HallOfFame, Logbook, MultiStatistics, ParetoFront, Statistics
 
 __all__ = ["cxTwoPoint", "cxBlend", "cxSimulatedBinaryBounded", "mutFlipBit", "mutGaussian",
            "mutPolynomialBounded", "selTournament", "selRandom",
            "selBest", "selWorst", "selNSGA2", "selTournamentDCD", "sortNondominated", "sortLogNondominated", "migRing", "Statistics",
-           "MultiStatistics", "Logbook", "HallOfFame", "initPopulation", "emo"]
+           "MultiStatistics", "Logbook", "HallOfFame", "ParetoFront", "initPopulation", "emo"]

@@ -589,4 +589,228 @@ class HallOfFame:
         return str(self.items)
 
 
-__all__ = ["Statistics", "MultiStatistics", "Logbook", "HallOfFame"]
+# ---------------------------------------------------------------------------
+# ParetoFront (deap/tools/support.py:591-640)
+# ---------------------------------------------------------------------------
+_GTYPE_NAME = {0: "bits", 1: "f32", 2: "f64"}
+
+
+class ParetoFront(HallOfFame):
+    """Every non-dominated individual that ever lived in the population
+    (``support.py:591-640``): ``maxsize`` is None, the hall is sorted
+    lexicographically (best first) and grows without bound on a continuous
+    front.
+
+    ``update(list of host individuals)`` runs the reference's loop on the
+    host.  ``update(DevicePopulation)`` keeps the archive on the GPU (two
+    buffers of the population's layout used in turn, grown geometrically) and
+    is one ``dm_pareto_update`` call: the loop's closed form for valid,
+    NaN-free fitnesses and value-equality ``similar`` (DESIGN.md
+    §ParetoFront).  Outside those preconditions the archive is fetched and
+    the host loop runs over ``population.to_individuals()``.
+
+    The container interface (``len``, indexing, iteration, ``keys``,
+    ``items``, ``str``) is served from a host copy fetched lazily after a
+    device update; ``len`` never fetches.  ``insert`` / ``remove`` / ``clear``
+    edit the host copy (go through them, not through the ``items`` list: the
+    next device update re-uploads after them, and after an ``insert`` checks
+    that the hall still is a front -- else it takes the host loop).  :meth:`front` hands the archive
+    out as a DevicePopulation without a host copy."""
+
+    def __init__(self, similar=operator.eq):
+        self._host_ok = True   # _items / _keys hold the archive
+        self._dev_ok = False   # the device buffers hold the archive
+        self._bufs = None      # [current, spare] DevicePopulation
+        self._unchecked = False  # insert() since the hall was last known to be a front
+        HallOfFame.__init__(self, None, similar)
+
+    # no split update: the update synchronises the host by nature, and the
+    # drivers call update() when this attribute is absent
+    @property
+    def update_begin(self):
+        raise AttributeError("ParetoFront has no update_begin")
+
+    # -- host copy -----------------------------------------------------------
+    @property
+    def items(self):
+        self._materialise()
+        return self._items
+
+    @items.setter
+    def items(self, value):
+        self._items = value
+
+    @property
+    def keys(self):
+        self._materialise()
+        return self._keys
+
+    @keys.setter
+    def keys(self, value):
+        self._keys = value
+
+    def _materialise(self):
+        """One fetch of the archive's rows into host individuals."""
+        if self.__dict__.get("_host_ok", True):
+            return
+        cur = self._bufs[0]
+        inds = cur.to_individuals() if len(cur) else []
+        self._items = inds
+        self._keys = [ind.fitness for ind in reversed(inds)]
+        self._host_ok = True
+
+    def __len__(self):
+        if self.__dict__.get("_host_ok", True):
+            return len(self._items)
+        return len(self._bufs[0])
+
+    def insert(self, item):
+        # the reference's insert() evicts nothing: the hall may hold a
+        # dominated entry afterwards, which the closed form does not cover
+        HallOfFame.insert(self, item)
+        self._dev_ok = False
+        self._unchecked = True
+
+    def remove(self, index):
+        HallOfFame.remove(self, index)
+        self._dev_ok = False
+
+    def clear(self):
+        HallOfFame.clear(self)
+        self._dev_ok = False
+
+    def __getstate__(self):
+        self._materialise()
+        state = HallOfFame.__getstate__(self)
+        state["_bufs"] = None  # device buffers stay behind
+        state["_dev_ok"] = False
+        return state
+
+    # -- update ----------------------------------------------------------------
+    def update(self, population):
+        from ..device import DevicePopulation
+        if isinstance(population, DevicePopulation):
+            if len(population) == 0:
+                return
+            if self.similar in _VALUE_SIMILAR and self._update_device(population):
+                return
+            population = population.to_individuals()
+        self._update_host(population)
+
+    def _update_host(self, population):
+        """support.py:621-640, the reference's loop (also the slow path of a
+        device update and the CPU-side oracle of the device path)."""
+        self._materialise()
+        self._dev_ok = False
+        items = self._items
+        for ind in population:
+            dominated = twin = False
+            beaten = []
+            for i, hofer in enumerate(items):
+                if not beaten and hofer.fitness.dominates(ind.fitness):
+                    dominated = True
+                    break
+                if ind.fitness.dominates(hofer.fitness):
+                    beaten.append(i)
+                elif ind.fitness == hofer.fitness and self.similar(ind, hofer):
+                    twin = True
+                    break
+            for i in reversed(beaten):
+                HallOfFame.remove(self, i)
+            if not dominated and not twin:
+                HallOfFame.insert(self, ind)
+
+    def _same_layout(self, pop):
+        cur = self._bufs[0] if self._bufs else None
+        return (cur is not None and cur.gtype == pop.gtype and cur.dim == pop.dim and
+                cur.weights == pop.weights and cur.device == pop.device)
+
+    def _upload(self, pop):
+        """Bring the device archive up to date with the host copy, in
+        ``pop``'s layout.  False when the host items cannot live there (another
+        layout, an invalid or NaN fitness): the caller takes the host loop."""
+        from ..device import DevicePopulation
+        if self._dev_ok and self._same_layout(pop):
+            return True
+        self._materialise()
+        items = self._items
+        if not items:
+            self._bufs = [pop.like(0, capacity=256), pop.like(0, capacity=256)]
+            self._dev_ok = True
+            self._unchecked = False
+            return True
+        for ind in items:
+            wv = ind.fitness.wvalues
+            if len(ind) != pop.dim or len(wv) != pop.nobj or any(w != w for w in wv) or \
+                    tuple(ind.fitness.weights) != pop.weights:
+                return False
+        cur = DevicePopulation.from_individuals(items, pop.weights, _GTYPE_NAME[pop.gtype],
+                                                pop.device, capacity=max(2 * len(items), 256))
+        cur.individual_class = pop.individual_class
+        if self.__dict__.get("_unchecked", True) and not self._is_front(cur, items):
+            return False
+        self._unchecked = False
+        self._bufs = [cur, pop.like(0, capacity=256)]
+        self._dev_ok = True
+        return True
+
+    @staticmethod
+    def _is_front(cur, items):
+        """Whether the uploaded hall is mutually non-dominated (the device
+        update's precondition): its first front is all of it."""
+        if len(items) < 2:
+            return True
+        if cur.nobj == 1:
+            return all(it.fitness.wvalues == items[0].fitness.wvalues for it in items)
+        from .emo import _sort
+        return _sort(cur, len(cur), True)[3] == len(cur)
+
+    def _update_device(self, pop):
+        """One dm_pareto_update; False when the closed form does not apply
+        (the archive is then on the host and marked stale on the device)."""
+        from .. import _lib
+        if not self._upload(pop):
+            return False
+        cur, out = self._bufs
+        need = len(cur) + len(pop)
+        if out.capacity < need:
+            out = self._bufs[1] = pop.like(0, capacity=max(need, 2 * out.capacity))
+        n_out = ctypes.c_int64(0)
+        c_out = out.c_pop(0, 0)
+        rc = _lib.load().dm_pareto_update(pop.ctx.bind(), ctypes.byref(cur.c_pop()),
+                                          ctypes.byref(pop.c_pop()), ctypes.byref(c_out),
+                                          out.capacity, ctypes.byref(n_out), None)
+        if rc == _lib.DM_ERR_UNSUPPORTED:
+            self._materialise()
+            self._dev_ok = False
+            return False
+        _lib.check(rc, "dm_pareto_update")
+        out.resize(n_out.value)
+        self._bufs = [out, cur]
+        self._host_ok = False
+        self._items = self._keys = None
+        return True
+
+    def front(self):
+        """The archive as a DevicePopulation of its own (no host copy): the
+        rows in the hall's order, best first."""
+        from .. import _lib
+        if not self._dev_ok:
+            if self._bufs is None and not self._items:
+                raise ValueError("empty ParetoFront with no device layout yet")
+            layout = self._bufs[0] if self._bufs else None
+            if layout is None:
+                from ..device import DevicePopulation
+                layout = DevicePopulation.from_individuals(self._items)
+            if not self._upload(layout):
+                raise ValueError("the hall's entries do not fit one device layout")
+        cur = self._bufs[0]
+        n = len(cur)
+        copy_ = cur.like(n, capacity=max(n, 1))
+        if n:
+            _lib.call("dm_gather", cur.ctx.bind(), ctypes.byref(cur.c_pop()), None,
+                      ctypes.byref(copy_.c_pop()))
+        return copy_
+
+
+__all__ = ["Statistics", "MultiStatistics", "Logbook", "HallOfFame", "ParetoFront"]

@@ -312,6 +312,19 @@ int dm_sel_tournament_dcd(dm_ctx* ctx, const dm_pop* pop, const double* crowd, i
                           dm_rng rng, int32_t mode, int32_t* perm1, int32_t* perm2,
                           uint8_t* coin, int32_t* out_idx);
 
+/* ---- Pareto archive (deap/tools/support.py:591-640) ----------------------- */
+/* ParetoFront.update (support.py:612-640) at population granularity.
+ * archive: the current front (n may be 0), mutually non-dominated, twin-free,
+ * in the reference's order (what an earlier call produced).  out: same layout,
+ * room for archive->n + pop->n rows, aliasing neither input.  Writes the new
+ * front to out in the reference's order, *n_out (host) rows (out->n is set to
+ * it), and src[i] = archive row (>= 0) or -(pop row) - 1 for out row i
+ * (device, may be NULL).  An invalid row or a NaN wvalue in pop or archive:
+ * DM_ERR_UNSUPPORTED, out untouched.  Host-synchronising (the size is data
+ * dependent). */
+int dm_pareto_update(dm_ctx* ctx, const dm_pop* archive, const dm_pop* pop,
+                     dm_pop* out, int64_t out_capacity, int64_t* n_out, int32_t* src);
+
 /* ---- bounded real-valued variation (NSGA-II example loop) ---------------- */
 /* Parameters of cxSimulatedBinaryBounded(eta, low, up) (crossover.py:291-360)
  * and mutPolynomialBounded(eta, low, up, indpb) (mutation.py:51-95).  low/up
